@@ -31,10 +31,16 @@ random index returns the same chunks for every query. Before each step (untimed)
 random vectors afterwards: every query retrieves 4 chunks of its own through the full 1M-row scan,
 as a real corpus would (``unique_chunks_retrieved`` = 4 x queries).
 
-After the timed steps (untimed, reported alongside): ``p50_ttft_c1_s`` - 8 queries one at a time, TTFT
-from query arrival to first token; and an open-loop run (Poisson arrivals at 0.8x the measured rate,
-``poisson``), both on the rank-local index shard. ``retrieval_breakdown_ms`` splits the per-step query
-path into embed / scan / prompt build / tokenize / add_request.
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up, times the K steps and prints the result line.
+``--dump-outputs DIR`` also writes what the last timed step returned to its callers (``DIR/<name>.npy``: the
+generated token ids, the retrieved rows and their relevance, the query embeddings; inputs are seeded, so two
+builds run with the same arguments can be compared output for output). ``retrieval_breakdown_ms`` splits the
+per-step query path into embed / scan / prompt build / tokenize / add_request.
+
+``--full`` adds, after the timed steps (untimed, reported alongside): ``p50_ttft_c1_s`` - ``--probe-c1`` queries
+one at a time, TTFT from query arrival to first token; an open-loop run (Poisson arrivals at 0.8x the measured
+rate, ``poisson``), both on the rank-local index shard; and ``--served-steps`` waves of the same workload through
+the chain server (``served``). ``vs_baseline_single_stream`` comes from the c1 probes, so it needs ``--full`` too.
 
 Notes: the KV prefix cache is off (every query prefills its full prompt); score_threshold is disabled (random-init embeddings give near-zero cosine to a random
 index; thresholding would drop every chunk); EOS is ignored so every query generates exactly
@@ -83,20 +89,31 @@ def parse():
                     help="fp8 = OCP e4m3fn KV cache (an option, not the headline configuration: the JSON line "
                          "reports it in config.kv_cache_dtype)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(config 2, in-process path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the untimed c1 / open-loop TTFT probes "
+                         "and the served (chain server) pass after the timed steps")
     ap.add_argument("--no-plant", action="store_true", help="do not plant per-query relevant chunks")
-    ap.add_argument("--no-probes", action="store_true", help="skip the untimed c1 / open-loop TTFT probes")
+    ap.add_argument("--no-probes", action="store_true", help="with --full: skip the untimed c1 / open-loop TTFT probes")
     ap.add_argument("--probe-c1", type=int, default=4,
                     help="queries of the concurrency-1 probe (each runs its full max_tokens: TTFT and TPOT)")
     ap.add_argument("--served-steps", type=int, default=3,
-                    help="after the timed in-process steps (config 2): this many POST /generate waves through the chain "
-                         "server, reported as the 'served' sub-object (0: skip)")
+                    help="with --full, after the timed in-process steps (config 2): this many POST /generate waves "
+                         "through the chain server, reported as the 'served' sub-object (0: skip)")
     ap.add_argument("--served", action="store_true",
                     help="drive the chain server instead of the engine: every query is a concurrent POST /generate "
                          "SSE stream (basic_rag example, in-process engines), TTFT measured at the client")
     from generativeaiexamples_amd.benchmarks import CONFIGS, module
     for c in CONFIGS:
         module(c).add_args(ap)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps only
+        args.no_probes, args.served_steps = True, 0
+    if args.dump_outputs and (args.config != 2 or args.served):
+        ap.error("--dump-outputs covers the in-process headline path (config 2 without --served)")
+    return args
 
 
 def _sync():
@@ -193,6 +210,24 @@ def run_probes(args, embedder, index, engine, build_requests, plant, unplant, ne
             "poisson": {"rate_qps_per_gpu": round(rate, 3), "queries": n, "achieved_qps_per_gpu": round(n / span, 3),
                         "p50_ttft_s": round(tt[len(tt) // 2], 4),
                         "p90_ttft_s": round(tt[min(len(tt) - 1, int(0.9 * len(tt)))], 4)}}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0):
+    """Write every array as <name>.npy (rank 0) or <name>_rank<r>.npy, float32 / float64. Beyond DUMP_LIMIT_BYTES
+    in all, each array keeps a fixed, seeded sample of its rows (the same rows on every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES / total))
+            a = a[np.sort(np.random.default_rng(2024).permutation(a.shape[0])[:keep])]
+        np.save(os.path.join(out_dir, name + (".npy" if rank == 0 else f"_rank{rank}.npy")), a)
 
 
 def synthetic_question(q: int) -> str:
@@ -356,6 +391,7 @@ def main():
         ntok = sum(len(r.output_ids) for r in reqs)
         short = [len(r.output_ids) for r in reqs if len(r.output_ids) != args.max_tokens]
         assert not short, f"{len(short)} queries generated != max_tokens ({short[:4]}): work would be skipped"
+        last_step.update(emb=emb, rel=rel, rows=rows, reqs=reqs)  # what this step's callers received
         plen = statistics.mean(len(r.prompt_ids) for r in reqs)
         return t1 - t0, ttft, ntok, plen, t_retrieved - t0
 
@@ -378,7 +414,7 @@ def main():
             torch.distributed.destroy_process_group()
         return
 
-    uniq = set()
+    uniq, last_step = set(), {}
     for w in range(args.warmup):
         dt, *_ = run_step(10_000 + w, new_phase())
         log(f"warmup {w}: {dt:.2f}s")
@@ -397,6 +433,16 @@ def main():
         log(f"step {s}: {dt:.3f}s  p50 TTFT {statistics.median(ttft):.3f}s  retrieval {rt * 1000:.1f} ms")
 
     stats1, phase1 = dict(engine.stats), dict(engine.phase_ms)  # the timed steps only (before the probes)
+    if args.dump_outputs:
+        import numpy as np
+
+        dump_outputs(args.dump_outputs, {
+            "output_ids": np.asarray([r.output_ids for r in last_step["reqs"]], np.float64),  # [batch, max_tokens]
+            "retrieved_rows": np.asarray(last_step["rows"], np.float64),                      # [batch, top_k]
+            "retrieval_relevance": last_step["rel"].float().cpu().numpy(),                    # [batch, top_k]
+            "query_embeddings": last_step["emb"].float().cpu().numpy(),                       # [batch, dim]
+        }, rank)
+        log(f"outputs of timed step {args.steps - 1} written to {args.dump_outputs}")
     if engine.host_timeline:  # GAI_HOST_TIMELINE=1: host gaps of the pipelined decode, last timed step
         tl = engine.host_timeline
         ch = sorted(e - s for n, s, e in tl if n == "chain")

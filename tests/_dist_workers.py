@@ -141,7 +141,11 @@ def ep_padded_worker(rank, world, port, out_dir):
     torch.save({"out": out.float(), "exp": exp.float(), "out1": out1.float()},
                os.path.join(out_dir, f"ep_padded_{rank}.pt"))
     dist.barrier()
-    dist.destroy_process_group()
+    # shutdown() also drops the context's references to the world / dp groups, so at 8 ranks no gloo group (and none
+    # of its threads) outlives destroy_process_group() into interpreter exit
+    from generativeaiexamples_amd.parallel import dist as gdist
+
+    gdist.shutdown()
 
 
 def sharded_index_worker(rank, world, port, out_dir, max_queries=None):

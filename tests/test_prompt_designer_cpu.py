@@ -11,7 +11,8 @@ from generativeaiexamples_amd.chain_server.connectors import Embeddings
 from generativeaiexamples_amd.chain_server.vectorstore import VectorStore
 from generativeaiexamples_amd.playground.prompt_designer import PromptConfigStore, PromptDesigner, build_messages
 
-REF_CFG = "/root/reference/community/llm-prompt-design-helper/config.yaml"
+# the reference's community/llm-prompt-design-helper/config.yaml
+REF_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "prompt_design_config.yaml")
 
 
 class _Emb(Embeddings):
@@ -35,7 +36,6 @@ class _LLM:
         yield messages[-1]["content"].upper()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CFG), reason="reference tree not present")
 def test_reads_reference_config_shape(tmp_path):
     st = PromptConfigStore(REF_CFG)
     assert "meta/llama3-70b-instruct" in st.models() and "default" not in st.models()

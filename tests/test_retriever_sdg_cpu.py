@@ -10,7 +10,8 @@ import pytest
 
 from generativeaiexamples_amd.evaluation import retriever_sdg as sdg
 
-REF_DATA = "/root/reference/nemo/retriever-synthetic-data-generation/data"
+# sample files of the reference's nemo/retriever-synthetic-data-generation/data
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference")
 
 
 def test_ir_metrics_hand_computed():
@@ -34,7 +35,6 @@ def test_parse_qa_blocks_reference_style():
     assert qas[0]["answers"][0]["text"] == "On February 5, 2015." and qas[0]["synthetic"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference sample data not mounted")
 def test_loads_reference_sample_formats():
     c = sdg.Corpus.load(os.path.join(REF_DATA, "sample_data_squad.json"), "squad")
     assert sum(1 for _ in c.paragraphs()) >= 1

@@ -232,9 +232,14 @@ def test_persisted_collections_reopen(tmp_path):
     assert again.search("kb", "Falcon sensor", 1)[0][0].metadata["filename"] == "falcon.txt"
 
 
-def test_launch_server_reports_exit():
+def test_launch_server_reports_exit(tmp_path, monkeypatch):
+    import tempfile
+
     from generativeaiexamples_amd.community.sizing_advisor.deploy import launch_server
 
+    # the server's log goes to the temporary directory under a fixed name: keep it in this test's own folder, so a
+    # log left there by another user's run cannot get in the way
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
     ev = list(launch_server("llama3-8b", port=9199, python="/bin/false", poll_s=0.05, timeout_s=10))
     assert ev[0]["status"] == "starting" and "--llm llama3-8b" in ev[0]["command"]
     assert ev[-1]["status"] == "error" and "exited with code 1" in ev[-1]["message"]
